@@ -22,6 +22,14 @@ and sound features, 768-d, 32 heads; csrc/seqattn.hip) in front of a 3+3-layer P
 fp32.  --workload anet_c3d measures configs[4], the long-video stress config (cfgs/anet_c3d_pdvc.yml: T=1024,
 C=500 C3D features, Q=300 queries, 2+2 layers, 512 videos per GPU).  The default (no flags) is the headline fp32
 line.
+
+A plain run sets up, warms up, times the --steps steps and prints the result line (metric, value, unit, ms_per_step,
+config).  --full adds the secondary measurements after the timed steps: per-kernel HIP-event timings (2 eager steps),
+the MSDA and GEMM rooflines (one profiled step), the drop-in operator's timing and the two CPU baselines.
+--dump-outputs DIR writes what the last timed step computed as DIR/<name>.npy (dump_outputs).  The inputs and the
+initial weights are seeded, and for the dump the last timed step starts again from that initial state (weights,
+optimizer moments, generators; put back with the clock stopped), so the same arguments give the same step every run
+and two builds can be compared array for array.
 """
 import argparse
 import glob
@@ -103,6 +111,15 @@ def parse():
                         "ActivityNet count distribution, caption lengths from 2 to 28 words -- one per step, padded to "
                         "fixed capacities (pdvc/batch_layout.py) so one captured step graph serves them all")
     p.add_argument("--stream-batches", type=int, default=4, help="distinct batches of the ragged stream")
+    p.add_argument("--full", action="store_true",
+                   help="after the timed steps also run the secondary measurements: per-kernel HIP-event timings, the "
+                        "MSDA and GEMM rooflines, the drop-in operator's timing and the CPU baselines (each can be "
+                        "switched off by its --no-... option); a plain run only times the steps")
+    p.add_argument("--dump-outputs", metavar="DIR", default=None,
+                   help="after the timed steps write what the last timed step computed as DIR/<name>.npy (float32): "
+                        "train: the total loss, every loss term and every parameter's gradient; eval: the model's output tensors (large arrays as a fixed seeded sample).  "
+                        "train: the last timed step starts again from the seeded initial weights, optimizer state and "
+                        "generators (restored with the clock stopped), so its result is the same every run")
     a = p.parse_args()
     a.frontend = None
     for k, v in WORKLOADS[a.workload].items():
@@ -430,6 +447,33 @@ def freeze_gc():
         gc.freeze()
 
 
+DUMP_SAMPLE = 8192  # elements written of a larger array
+DUMP_LIMIT = 64 * 2 ** 20  # bytes, all files of one dump
+
+
+def dump_outputs(directory, arrays):
+    """--dump-outputs: every (name, tensor) of `arrays` as directory/<name>.npy, float32 (float64 tensors stay
+    float64).  An array of more than DUMP_SAMPLE elements is written as a fixed sample of its flattened elements, in
+    index order, the indices drawn by a generator seeded from the array's name and size -- two builds given the same
+    arguments write the same elements.  At most DUMP_LIMIT bytes in all."""
+    import zlib
+    os.makedirs(directory, exist_ok=True)
+    written = 0
+    for name, t in arrays:
+        t = t.detach().reshape(-1)
+        n = t.numel()
+        if n > DUMP_SAMPLE:
+            rng = np.random.RandomState(zlib.crc32(f"{name}:{n}".encode()))
+            idx = np.sort(rng.choice(n, DUMP_SAMPLE, replace=False))
+            t = t[torch.from_numpy(idx).to(t.device)]
+        x = t.to(torch.float64 if t.dtype == torch.float64 else torch.float32).cpu().numpy()
+        if written + x.nbytes > DUMP_LIMIT:
+            raise SystemExit(f"bench.py --dump-outputs: {name} would take the dump past {DUMP_LIMIT} bytes")
+        np.save(os.path.join(directory, name + ".npy"), x)
+        written += x.nbytes
+    log(f"wrote {len(arrays)} arrays ({written} bytes) to {directory}")
+
+
 def eval_main(a):
     """Evaluation throughput: forward with greedy captions for all Q queries (LSTM_DSA.py:118-186, the loop stops
     when every row has finished: tested on the device, read back a few steps late, the decode cut at the reference's
@@ -451,12 +495,14 @@ def eval_main(a):
     tr = Translator.from_vocab({str(i): f"w{i}" for i in range(1, vocab)})
     loader = types.SimpleNamespace(dataset=types.SimpleNamespace(translator=tr))
     steps_seen = []
+    last_out = [None]  # the model's outputs of the latest step (--dump-outputs)
 
     def step():
         with torch.no_grad():
             out, _ = model(dt, criterion, "queries", eval_mode=True)
             res = post(out, dt["video_length"][:, 1], loader)
         steps_seen.append(out["seq"].shape[-1] if len(out["seq"]) else 0)
+        last_out[0] = out
         return res
 
     # PostProcess's host half runs on a worker thread (pdvc.py DeferredRow) while this thread queues the next batch;
@@ -487,6 +533,9 @@ def eval_main(a):
     ws, ds = sorted(walls), sorted(devs)
     med = ws[len(ws) // 2] if len(ws) % 2 else 0.5 * (ws[len(ws) // 2 - 1] + ws[len(ws) // 2])
     dmed = ds[len(ds) // 2] if len(ds) % 2 else 0.5 * (ds[len(ds) // 2 - 1] + ds[len(ds) // 2])
+    if a.dump_outputs:
+        dump_outputs(a.dump_outputs, [(k, v) for k, v in sorted((last_out[0] or {}).items())
+                                      if isinstance(v, torch.Tensor) and v.numel()])
     result = {"metric": "videos/sec eval (PDVC forward + greedy captions of all queries + PostProcess, "
                         f"T={a.T} C={a.C} Q={a.Q}) on 1 MI355X",
               "value": a.steps * B / el, "unit": "videos/s", "n_gpus": 1, "steps": a.steps, "warmup": a.warmup,
@@ -616,6 +665,7 @@ def main():
     from pdvc.precision import bf16_matmul
     bf16 = a.precision == "bf16"
     step_no = [0]
+    last_losses = [None]  # the eager step's loss terms (--dump-outputs)
 
     def next_batch():
         if stream is not None:
@@ -626,6 +676,7 @@ def main():
     def fwd_bwd():
         out, loss = model(cur[0], criterion, "queries")
         total = sum(loss[k] * wd[k] for k in loss.keys() if k in wd)
+        last_losses[0] = loss
         if reducer is not None:
             reducer.zero_grad()  # bucket-resident gradients (pdvc/distributed.py): one fill per bucket
         else:
@@ -670,6 +721,23 @@ def main():
                 torch.cuda.synchronize()
                 print("debug: adam ok", file=sys.stderr, flush=True)
             return total
+    rewind = None
+    if a.dump_outputs:
+        # The step's kernels sum with float atomics, and the optimizer carries that rounding noise from step to step,
+        # so after a few steps two runs hold visibly different weights.  For the dump the last timed step therefore
+        # starts from the run's seeded initial state -- the weights as built, AdamW's moments and step count at zero,
+        # the generators reseeded -- put back with the clock stopped: it does a timed step's work on inputs that are
+        # the same every run, and two builds can be compared on what it computes.
+        start = [p.detach().clone() for p in params]
+
+        def rewind():
+            with torch.no_grad():
+                torch._foreach_copy_(params, start)
+                for st in opt.state.values():
+                    for v in st.values():
+                        if isinstance(v, torch.Tensor):
+                            v.zero_()
+            torch.manual_seed(1)
     log(f"{B} videos/GPU, {world} rank(s): warm-up")
     for _ in range(a.warmup):
         step()
@@ -686,21 +754,39 @@ def main():
     if world > 1:
         dist.barrier()
     torch.cuda.synchronize()
-    if not graphed:
+    if a.full and not graphed:
         _native.TIMER = timer  # eager: HIP events around every launch of the timed steps themselves
     t0 = time.perf_counter()
-    for _ in range(a.steps):
+    paused = 0.0
+    for i in range(a.steps):
+        if rewind is not None and i == a.steps - 1:  # --dump-outputs: the clock stops while the state is put back
+            torch.cuda.synchronize()
+            p0 = time.perf_counter()
+            rewind()
+            torch.cuda.synchronize()
+            paused = time.perf_counter() - p0
         step()
     torch.cuda.synchronize()
-    el = time.perf_counter() - t0
+    el = time.perf_counter() - t0 - paused
     _native.TIMER = None
     if world > 1:
         dist.barrier()
         t = torch.tensor([el], device=device)
         dist.all_reduce(t, op=dist.ReduceOp.MAX)
         el = float(t.item())
+    if a.dump_outputs and rank == 0:
+        # what the last timed step (started from the seeded initial state, `rewind`) left with its caller: the total
+        # loss, the loss terms and every parameter's gradient (clipped, averaged over ranks).  The weights after the
+        # optimizer step are not written: AdamW's first update is lr * g / (|g| + eps), which turns the atomics'
+        # rounding on the near-zero gradients of zero-initialised weights into differences of 1e-3 of the update
+        # from run to run, where the gradients themselves agree to 1e-6
+        losses = sg.losses if sg is not None else (last_losses[0] or {})
+        arrays = [("loss_total", sg.total if sg is not None else sum(losses[k] * wd[k] for k in losses if k in wd))]
+        arrays += [("loss." + k, v) for k, v in sorted(losses.items()) if isinstance(v, torch.Tensor)]
+        arrays += [("grad." + n, p.grad) for n, p in model.named_parameters() if p.grad is not None]
+        dump_outputs(a.dump_outputs, arrays)
     timing_note = "HIP events around every launch in the timed steps"
-    if graphed:
+    if a.full and graphed:
         # the timed steps replay the kernels inside a hipGraph, where no event can bracket one launch:
         # time them in 2 untimed eager steps at the same shapes right after (same kernels, same data sizes)
         model.__dict__.pop("_graphed_trunk", None)
@@ -713,7 +799,7 @@ def main():
                        "same shapes; step wall time excludes them")
         if stream is not None:
             timing_note += " (eager steps on the capacity-padded batches)"
-    ks = timer.summary()
+    ks = timer.summary()  # empty in a plain run: every per-kernel figure below belongs to --full
     for base in ("pdvc_msda1d_forward_f32", "pdvc_msda1d_backward_ex_f32"):  # one entry per MSDA pass, either form
         extra = ks.pop(base + "_bf16out", None)
         if extra:
@@ -722,10 +808,12 @@ def main():
                 d[k] += extra[k]
             d["metas"] += extra["metas"]
             d["launch_ms"] += extra["launch_ms"]
-    log("GEMM roofline step")
-    groof = None if a.no_gemm_roofline else gemm_roofline(fwd_bwd, step, a.precision, graphed)
+    groof = None
+    if a.full and not a.no_gemm_roofline:
+        log("GEMM roofline step")
+        groof = gemm_roofline(fwd_bwd, step, a.precision, graphed)
     dropin = None
-    if rank == 0 and not a.frontend and stream is None and not a.no_dropin:
+    if a.full and rank == 0 and not a.frontend and stream is None and not a.no_dropin:
         log("drop-in operator timing")
         dropin = dropin_msda(a.T)
     videos = a.steps * B * world
@@ -863,8 +951,9 @@ def main():
         result["config"]["graph_nodes_per_replay"] = dict(getattr(sg, "node_counts", {}),
                                                           memsets_rewritten=getattr(sg, "memsets_replaced", None))
     ksteps = 2 if graphed else a.steps
-    result["kernels"] = {n: {"launches": v["launches"], "avg_us": 1e3 * v["ms"] / max(v["launches"], 1),
-                             "share_of_step": v["ms"] / ksteps / (1e3 * el / a.steps)} for n, v in ks.items()}
+    if a.full:
+        result["kernels"] = {n: {"launches": v["launches"], "avg_us": 1e3 * v["ms"] / max(v["launches"], 1),
+                                 "share_of_step": v["ms"] / ksteps / (1e3 * el / a.steps)} for n, v in ks.items()}
     # the north-star comparison, like for like: MSDeformAttn fwd+bwd (the fused 1-D kernels, encoder + decoder
     # calls) per step on the GPU, from the HIP-event timings above, as videos/s against the CPU figure
     msda_ms = sum(ks[n]["ms"] for n in ("pdvc_msda1d_forward_f32", "pdvc_msda1d_backward_ex_f32") if n in ks) / ksteps
@@ -872,7 +961,7 @@ def main():
         result["msda_gpu"] = {"ms_per_step": msda_ms, "videos_per_s": B / (msda_ms * 1e-3) * world,
                               "what": "fused MSDeformAttn forward + backward kernels of every encoder and decoder "
                                       "layer, HIP events, per step of B videos per GPU"}
-    if rank == 0 and world == 1 and not a.no_cpu_baseline:
+    if a.full and rank == 0 and world == 1 and not a.no_cpu_baseline:
         log("CPU baseline (reference core, torch)")
         result["cpu_baseline"] = cpu_baseline(a, args.enc_layers, args.dec_layers)
         log("CPU baseline (C oracle)")

@@ -132,7 +132,7 @@ _DP_OVERLAP = []
 _DP_TRIALS = []
 
 
-def dp_overlap_supported():
+def dp_overlap_supported(side=None):
     """Whether an event recorded inside a stream capture (GraphEvent, hipEventRecordExternal) gates a stream outside
     the graph on this stack -- probed once, deterministically.  The probe graph first runs a kernel that holds its
     stream until the host sets a flag (pdvc_spin_until_flag: fine-grained pinned memory, bounded at 5 s), then writes
@@ -141,7 +141,8 @@ def dp_overlap_supported():
     must finish and read 0 (the side stream does run beside a held replay) and the waited copy must not have
     finished; released, it must read 7 or 3.  A record that does not gate fails the second test every time, not by
     timing (the earlier probe's ungated control could read 3 when the replay happened to finish
-    first).  PDVC_DP_OVERLAP=0 turns the overlap off."""
+    first).  PDVC_DP_OVERLAP=0 turns the overlap off.  `side`: the side stream to probe with (default: the next
+    stream of torch's pool)."""
     if os.environ.get("PDVC_DP_OVERLAP", "1") == "0":
         return False
     if not _DP_OVERLAP:
@@ -168,7 +169,7 @@ def dp_overlap_supported():
                 mark.fill_(3.0)
             if not recorded:
                 raise RuntimeError("the event record was refused inside the capture")
-            side = torch.cuda.Stream()
+            side = torch.cuda.Stream() if side is None else side
             trials = []
             for _ in range(2):
                 flag.value = 0

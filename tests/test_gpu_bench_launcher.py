@@ -16,8 +16,8 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 def test_bench_starts_two_ranks_itself():
     env = {k: v for k, v in os.environ.items() if k not in ("WORLD_SIZE", "RANK", "LOCAL_RANK")}
     cmd = [sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "2", "--same-device", "--dist-backend", "gloo",
-           "--videos-per-gpu", "4", "--steps", "2", "--warmup", "1", "--no-cpu-baseline", "--no-dropin",
-           "--no-gemm-roofline"]
+           "--videos-per-gpu", "4", "--steps", "2", "--warmup", "1", "--full", "--no-cpu-baseline", "--no-dropin",
+           "--no-gemm-roofline"]  # --full: the eager kernel-timing steps after the replays run on both ranks too
     r = subprocess.run(cmd, env=env, capture_output=True, text=True, timeout=600)
     assert r.returncode == 0, r.stderr[-4000:]
     lines = [l for l in r.stdout.splitlines() if l.startswith("{")]

@@ -6,7 +6,7 @@ OUT=gpurun_out/$1; mkdir -p "$OUT"
 run() {  # name, seconds, bench.py arguments
   local n=$1 s=$2; shift 2
   echo "[$(date +%T)] $n: bench.py $*"
-  timeout -k 10 "$s" python -u bench.py "$@" > "$OUT/bench_$n.json" 2> "$OUT/bench_$n.err" \
+  timeout -k 10 "$s" python -u bench.py --full "$@" > "$OUT/bench_$n.json" 2> "$OUT/bench_$n.err" \
       || { echo "$n failed"; tail -20 "$OUT/bench_$n.err"; exit 1; }
   python -c "import json,sys; d=json.load(open('$OUT/bench_$n.json')); print('  $n', round(d['value'], 1), d['unit'])"
 }

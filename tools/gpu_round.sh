@@ -54,13 +54,13 @@ if has tests; then
 fi
 if has bench; then
   echo "[$(date +%T)] bench"
-  timeout -k 10 400 python -u bench.py $BENCH_ARGS > "$OUT/bench.json" 2> "$OUT/bench.err" \
+  timeout -k 10 400 python -u bench.py --full $BENCH_ARGS > "$OUT/bench.json" 2> "$OUT/bench.err" \
       || { echo "bench failed"; tail -30 "$OUT/bench.err"; exit 1; }
   cat "$OUT/bench.json"
 fi
 if has gemm; then
   echo "[$(date +%T)] bench --gemm hip"
-  timeout -k 10 400 python -u bench.py --gemm hip --no-cpu-baseline > "$OUT/bench_gemm_hip.json" \
+  timeout -k 10 400 python -u bench.py --full --gemm hip --no-cpu-baseline > "$OUT/bench_gemm_hip.json" \
       2> "$OUT/bench_gemm_hip.err" || { echo "bench --gemm hip failed"; tail -30 "$OUT/bench_gemm_hip.err"; exit 1; }
   cat "$OUT/bench_gemm_hip.json"
   timeout -k 10 300 python -u tools/gemmbench.py > "$OUT/gemmbench.txt" 2>&1 \
@@ -70,7 +70,7 @@ fi
 if has prof; then
   echo "[$(date +%T)] rocprofv3 kernel stats"
   timeout -k 10 400 rocprofv3 --kernel-trace --stats --output-format csv -d "$OUT/prof" -o run \
-      -- python -u bench.py --steps 5 --warmup 2 --no-cpu-baseline --no-dropin $BENCH_ARGS > "$OUT/prof_bench.json" 2> "$OUT/prof.err" \
+      -- python -u bench.py --full --steps 5 --warmup 2 --no-cpu-baseline --no-dropin $BENCH_ARGS > "$OUT/prof_bench.json" 2> "$OUT/prof.err" \
       || { echo "rocprof failed"; tail -30 "$OUT/prof.err"; exit 1; }
   ks=$(find "$OUT/prof" -name "*kernel_stats.csv" | head -1)
   if [ -n "$ks" ]; then python tools/profsum.py "$ks" 0 45 > "$OUT/prof_summary.txt"; cat "$OUT/prof_summary.txt"; fi
@@ -81,7 +81,7 @@ if has pmc; then
     [ $c = WRITE_SIZE ] && d=write
     echo "[$(date +%T)] pmc $c"
     timeout -s KILL 300 rocprofv3 --pmc $c --kernel-include-regex msda1d_fwd --output-format csv \
-        -d "$OUT/pmc/$d" -- python -u bench.py --steps 2 --warmup 1 --no-cpu-baseline \
+        -d "$OUT/pmc/$d" -- python -u bench.py --full --steps 2 --warmup 1 --no-cpu-baseline \
         > "$OUT/pmc_$d.json" 2> "$OUT/pmc_$d.err" || { echo "pmc $c failed"; tail -20 "$OUT/pmc_$d.err"; exit 1; }
   done
   python tools/pmc_traffic.py "$OUT/pmc" msda1d_fwd "$OUT/msda1d_fwd_traffic.json"
